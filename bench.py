@@ -2,13 +2,16 @@
 """bench.py -- voxels/s of the XLSTM-HVED forward+backward hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp16|fp32] [--size 128] [--no-graph] [--no-cpu]
+                    [--dump-outputs DIR]
 
 One process per GPU.  Under torch.distributed.run RANK/LOCAL_RANK/WORLD_SIZE are read from the environment; a plain
 `python bench.py --gpus N` (no launcher) spawns its own N worker processes before anything touches a GPU.  A step = one forward + backward of XLSTM_HVED (train mode, all 4 modalities, recon=True, loss of
 SURVEY.md 8(d)) on one synthetic 1x4x128^3 patch per rank, plus for N>1 the flat RCCL all-reduce of the generator's
 gradients (data parallel; weak scaling).  Forward+backward are captured once into a hipGraph and replayed (the
 all-reduce is issued eagerly after each replay, on the same stream); W warm-up steps, then exactly K timed steps
-between barrier + synchronize pairs; the slowest rank's time is used.
+between barrier + synchronize pairs (each one pass; --inner R > 1 replays R passes per timed step, --inner 0 sizes R from a
+probe); the slowest rank's time is used.  --dump-outputs DIR writes the last timed step's outputs as .npy files: the inputs,
+weights and noise seeds are fixed, so two runs (or two builds) with the same arguments can be compared output for output.
 
 Rank 0 prints ONE JSON line.  Extra objects:
   roofline      dominant conv kernel of the step (by total time), timed per launch with HIP events on the launch stream
@@ -73,9 +76,13 @@ def parse():
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--inner", type=int, default=0,
-                    help="passes per timed step (0 = sized so that the timed region lasts --min-timed-s; 1 = the plain K-step loop)")
-    ap.add_argument("--min-timed-s", type=float, default=5.0)
+    ap.add_argument("--inner", type=int, default=1,
+                    help="passes per timed step (1 = the plain K-step loop: --steps K timed passes; 0 = sized from a probe so "
+                         "that the timed region lasts --min-timed-s)")
+    ap.add_argument("--min-timed-s", type=float, default=5.0, help="with --inner 0: the timed region's target length")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy "
+                         "(rank 0; float32, <= 64 MB in all; arrays above 2^20 elements as a fixed seeded sample)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--force-dist", action="store_true",
@@ -87,7 +94,8 @@ def parse():
     ap.add_argument("--no-trainstep", action="store_true", help="skip timing the whole training step (train.py:208-296)")
     ap.add_argument("--wgrad-overlap", action="store_true",
                     help="launch the weight-gradient kernels on a second HIP stream (measured on MI355X: no gain, 9.88-10.7 ms "
-                         "vs 9.96 ms -- the hipGraph's cross-stream dependencies cost what the overlap saves; off by default)")
+                         "vs 9.96 ms -- the hipGraph's cross-stream dependencies cost what the overlap saves; off by default; eager launches only: "
+                         "inert under capture, use with --no-graph)")
     ap.add_argument("--no-wgrad-defer", action="store_true",
                     help="launch every weight gradient where backward reaches it instead of batching them at the end of backward")
     ap.add_argument("--wgrad-batch", type=int, default=12, help="weight-gradient calls forked to the side stream per batch")
@@ -154,6 +162,30 @@ def cpu_baseline(size, batch, threads=CPU_BASELINE_THREADS):
                       + f"; value = the faster ({cores} threads); timed in a child process next to the GPU legs of this run"}
 
 
+DUMP_SAMPLE = 1 << 20       # elements kept of a larger output (--dump-outputs)
+DUMP_SEED = 1234
+
+
+def dump_outputs(path, outs):
+    """Writes each output of the timed path's last step as <path>/<name>.npy in float32: the segmentation probabilities, the
+    reconstruction, mu / logvar of every latent level, the loss and the flat fp32 gradient bucket of the generator (after the
+    all-reduce for N > 1).  An array above DUMP_SAMPLE elements is stored as the sample at DUMP_SAMPLE sorted flat indices drawn
+    from a generator seeded with DUMP_SEED and the array's size, so two runs and two builds keep the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in outs.items():
+        a = t.detach().float().flatten()
+        if a.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(DUMP_SEED + a.numel())
+            idx = torch.randperm(a.numel(), generator=g)[:DUMP_SAMPLE].sort().values
+            a = a[idx.to(a.device)]
+        a = a.cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+
+
 def spawn_workers(args):
     """`python bench.py --gpus N` without a launcher: start N fresh worker processes of this script (one per GPU, RCCL
     rendezvous on 127.0.0.1) BEFORE this process touches a GPU, relay rank 0's JSON line, exit with the worst code."""
@@ -181,6 +213,8 @@ def spawn_workers(args):
 
 def main():
     args = parse()
+    if args.dump_outputs and args.inner == 0:
+        raise SystemExit("--dump-outputs needs a fixed pass count: the noise advances per pass, --inner 0 sizes it from a timing probe")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(args.size, args.batch)))
         return
@@ -240,7 +274,7 @@ def main():
     ops.set_wgrad_overlap(args.wgrad_overlap, args.wgrad_batch)
     ops.set_wgrad_defer(not args.no_wgrad_defer and not args.wgrad_overlap)   # weight gradients batched at the end of backward           # weight gradients on a second HIP stream, joined once per step
 
-    def make_compute(xin, split=False):
+    def make_compute(xin, split=False, keep=None):
         # fp16 storage: the activation gradients need the caller's loss scaling, as the reference's GradScaler provides
         # (train.py:207,265-268; initial scale 65536); the unscale of the fp32 parameter gradients is part of the step.
         # split (fp32_mfma): fp32 storage, but the activation gradients enter the matrix cores as fp16 pairs -- same scale
@@ -257,8 +291,12 @@ def main():
             ops.join_wgrad_stream()                           # the weight-gradient branch rejoins the step here
             if scale != 1.0:
                 grads.flat.mul_(1.0 / scale)
+            if keep is not None:                              # under capture: the graph's own output tensors, rewritten by every replay
+                keep.update(seg=seg, rec=rec[0], loss=loss, grad=grads.flat,
+                            **{f"mu{l}": t for l, t in enumerate(mu)}, **{f"logvar{l}": t for l, t in enumerate(lv)})
         return compute
-    compute = make_compute(x, args.dtype == "fp32_mfma")
+    last = {} if args.dump_outputs else None                  # the last step's outputs (--dump-outputs)
+    compute = make_compute(x, args.dtype == "fp32_mfma", last)
 
     def step():
         compute()
@@ -295,9 +333,9 @@ def main():
     for _ in range(args.warmup):
         run()
     sync_all()
-    # Inner repeats: the driver's K may be small (20 steps = 0.08 s of GPU time, invisible to its utilisation sampler), so
-    # each of the K timed steps replays the pass `inner` times, sized from a short probe so that the timed region lasts
-    # >= --min-timed-s; ms_per_step and value are per PASS (one forward + backward [+ all-reduce]), inner_repeats is reported.
+    # Inner repeats (opt-in): each of the K timed steps replays the pass `inner` times; --inner 0 sizes it from a short probe
+    # so that the timed region lasts >= --min-timed-s.  ms_per_step and value are per PASS (one forward + backward
+    # [+ all-reduce]), inner_repeats is reported.
     inner = max(1, args.inner)
     if args.inner == 0:
         t0 = time.perf_counter()
@@ -321,6 +359,8 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     passes = args.steps * inner
     ms = dt / passes * 1e3
     value = world * B * S ** 3 / (dt / passes)

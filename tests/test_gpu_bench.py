@@ -38,6 +38,29 @@ def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
     assert 1000 < hs["copy"] < 8000 and 1000 < hs["add_2r1w"] < 8000, hs
 
 
+def test_bench_dump_outputs_are_the_last_step_and_repeat_across_runs(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float32 .npy files, <= 64 MB, --steps K timed passes exactly;
+    two runs with the same arguments see the same inputs and give the same outputs up to the order of fp32 atomics."""
+    import numpy as np
+    dumps = []
+    for r_ in range(2):
+        d = tmp_path / f"run{r_}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--size", "64", "--no-cpu",
+                            "--no-roofline", "--no-modes", "--no-config3", "--no-trainstep", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads(r.stdout.strip().splitlines()[-1])
+        assert j["steps"] == 2 and j["inner_repeats"] == 1
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    a, b = dumps
+    assert set(a) == {"seg", "rec", "loss", "grad"} | {f"{k}{l}" for k in ("mu", "logvar") for l in range(4)}, sorted(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k, v in a.items():
+        assert v.dtype == np.float32 and v.shape == b[k].shape and np.isfinite(v).all(), k
+        scale = max(float(np.abs(v).max()), 1e-12)
+        assert float(np.abs(v - b[k]).max()) <= 1e-2 * scale, (k, float(np.abs(v - b[k]).max()) / scale)
+
+
 def test_bench_force_dist_rccl_allreduce_with_graph_capture():
     """The N>1 code path on one GPU: RCCL communicator, thread-local hipGraph capture of the step, the flat-bucket
     all-reduce issued after every replay (bench.py --force-dist)."""

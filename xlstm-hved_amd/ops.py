@@ -752,7 +752,7 @@ def conv3d_dgrad_s2(dy, weights, *, cin, in_spatial, groups=1, e=None, red=None)
 # stream at the call (everything issued so far -- dY, the saved input, the zeroed gradient bucket -- is ordered before
 # it) and is joined once, by join_wgrad_stream(), before the gradients are consumed.  The small-volume weight gradients
 # are latency-bound (a few dozen workgroups): next to the data-gradient chain they cost almost nothing.  Inside a hipGraph
-# capture the fork/join becomes a parallel branch of the graph.  Only calls whose targets are existing .grad buffers
+# capture the switch is inert (conv3d_wgrad): the step is captured on one stream.  Only calls whose targets are existing .grad buffers
 # (functional._targets "direct" accumulation, e.g. parallel.FlatGrads) may overlap: a freshly allocated gradient that
 # autograd consumes on the compute stream must be complete when backward() returns it.
 _WG = {"on": False, "streams": {}, "keep": [], "forked": set(), "pending": [], "batch": 12, "defer": False, "deferred": [],
@@ -845,7 +845,10 @@ def conv3d_wgrad(xa, xb, dy, dws, dbs, *, k, stride=1, groups=1, pre=None, side=
         _WG["deferred"].append(_wgrad_call(xa, xb, dy, dws, dbs, k, stride, groups, pre, bcast))
         _WG["maxvol"] = max(_WG["maxvol"], vol)
         return
-    if side and _WG["on"] and xa.is_cuda:
+    # Under stream capture the side stream is INERT, like set_level_streams: the fork would make the weight gradients a parallel
+    # branch of the graph, and replaying that graph crashed the host inside hipGraphLaunch.  The captured step launches them
+    # in order on the capture stream.
+    if side and _WG["on"] and xa.is_cuda and not torch.cuda.is_current_stream_capturing():
         _WG["pending"].append((xa, xb, dy, dws, dbs, dict(k=k, stride=stride, groups=groups, pre=pre, bcast=bcast), current_arith()))
         if len(_WG["pending"]) >= _WG["batch"]:
             _flush_wgrads()
