@@ -703,6 +703,25 @@ int xh_scalar_lincomb(void* stream, int n, const void* const* src, const int* is
 int xh_scalar_fanout(void* stream, int n, const double* coef, const float* g, float* out32, double* out64);
 
 /* ------------------------------------------------------------------------------------------------
+ * HD95 region metric (metrics.py:311-406: getHausdorff's channel map, the surface / distance / percentile definition that
+ * getHausdorff and getHausdorff_KD share) for ONE sample and the three sigmoid regions at once (csrc/hd95.hip).
+ * ------------------------------------------------------------------------------------------------ */
+#define XH_U8 3                   /* target storage: uint8 / bool, one byte per voxel */
+/* Bytes of the xh_hd95 workspace for a D x H x W volume (unit_spacing: all three spacings 1.0); -1 for an unsupported
+ * extent (W > 512, H or D > 65535). */
+long long xh_hd95_workspace_bytes(int D, int H, int W, int unit_spacing);
+/* Region r in {WT 0, TC 1, EC 2}: a = input[r] > 0.5 (compared in the storage dtype XH_F32 / XH_BF16 / XH_F16), b = target[r] != 0
+ * (XH_F32, XH_BF16, XH_F16 or XH_U8).  input / target point at channel 0 of the sample; channel r starts r * *_cstride elements
+ * further, each a contiguous D x H x W block.  S(m) = voxels where any of the three integer Sobel responses of m (zero padding 1)
+ * is non-zero; point coordinates are (d, h, w) * (s0, s1, s2).  out[r] (fp64) = max(P95 of the distances from S(b) to S(a),
+ * P95 of those from S(a) to S(b)) with np.percentile's 'linear' rule, or 0 when S(a) or S(b) is empty.  counts (optional, int64):
+ * [|S(a_WT)|, |S(b_WT)|, |S(a_TC)|, |S(b_TC)|, |S(a_EC)|, |S(b_EC)|].  Six launches (seven at unit spacing), no host synchronisation; the library
+ * initialises the workspace itself (ws_bytes >= xh_hd95_workspace_bytes). */
+int xh_hd95(void* stream, int in_dtype, const void* input, long long in_cstride, int tgt_dtype, const void* target,
+            long long tgt_cstride, int D, int H, int W, double s0, double s1, double s2, void* ws, long long ws_bytes, double* out,
+            long long* counts);
+
+/* ------------------------------------------------------------------------------------------------
  * Discriminator (RA_HVED.py:204-236, buildingblocks.py:342-358): convolutions 7 -> 64 -> 128 -> 256 -> 512 -> 1 with kernel
  * size ks = 4 (train.py:146, Pretrain.py:150) or 3 (the class default), padding 1, strides 1,2,2,2,1, as implicit GEMMs on the
  * matrix cores.  Inside the discriminator activations are CHANNELS-LAST [N][D][H][W][C], 16-bit (dtype XH_BF16 / XH_F16),

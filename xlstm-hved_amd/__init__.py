@@ -15,8 +15,9 @@ from .model import (MODELS, SUBSETS_MODALITIES, AbstractFusion3DUNet, ReconDecod
 from .utils import init_weights, seed_everything, subset_idx  # noqa: F401
 from . import inference, losses  # noqa: F401
 from .losses import (DiceCoefficient, DiceLoss, DiceRegion, GANLoss, MSELoss, combine, compute_KLD, compute_KLD_levels,  # noqa: F401
-                     gan_pair_loss, mse_loss, nested_attention)
-from .inference import eval_overlap_volume  # noqa: F401
+                     gan_pair_loss, getHausdorff, getHausdorff_KD, hd95_regions, mse_loss,
+                     nested_attention)
+from .inference import eval_overlap_metrics, eval_overlap_volume  # noqa: F401
 
 TRAIN_KWARGS = dict(multi_stream=4, fusion_level=4, shared_recon=True, recon_skip=True, MVAE_reduction=True,
                     final_sigmoid=True, f_maps=4, layer_order="ilc")      # train.py:142-143

@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libxlstm_hved_hip.so")
 
 XH_F32, XH_BF16, XH_F16 = 0, 1, 2
+XH_U8 = 3                                    # uint8 / bool storage (xh_hd95 targets)
 ARITH_F32_SPLIT, ARITH_K7_VECTOR = 1, 2      # xh_conv_desc.arith bits
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID = 0, 1, 2, 3
 
@@ -198,6 +199,8 @@ SIGNATURES = {
     "xh_loss_finalize": (I, [vp, I, vp, I, I, C.c_double, C.c_double, vp, vp, vp]),
     "xh_kld_fwd": (I, [vp, I, vp, vp, vp, I, I, ll, vp]),
     "xh_kld_bwd": (I, [vp, I, vp, vp, vp, I, I, ll, F, vp, vp, vp]),
+    "xh_hd95_workspace_bytes": (ll, [I, I, I, I]),
+    "xh_hd95": (I, [vp, I, vp, ll, I, vp, ll, I, I, I, C.c_double, C.c_double, C.c_double, vp, ll, vp, vp]),
     "xh_nested_weight": (I, [vp, I, vp, ll, vp, ll, I, ll]),
     "xh_fill": (I, [vp, I, vp, ll, F, vp]),
     "xh_scalar_lincomb": (I, [vp, I, vp, vp, vp, vp]),

@@ -152,3 +152,15 @@ def eval_overlap_volume(model, x, subset_idx=14, patch_size=(128, 128, 128), ove
         dist.all_reduce(sum_tot, group=group)
         dist.all_reduce(count_tot, group=group)
     return sum_tot / count_tot
+
+
+@torch.no_grad()
+def eval_overlap_metrics(model, x, mask, subset_idx=14, **kwargs):
+    """The per-volume row of evaluation.py:380-398 on the device: (2, 3) fp64 [[Dice WT, TC, EC], [HD95 WT, TC, EC]] of the
+    overlap-averaged probabilities of eval_overlap_volume(model, x, subset_idx, **kwargs) against mask (1, 3, D, H, W)."""
+    from .losses import DiceRegion, hd95_regions
+    prob = eval_overlap_volume(model, x, subset_idx=subset_idx, **kwargs)
+    if tuple(mask.shape) != tuple(prob.shape):
+        raise ValueError(f"mask shape {tuple(mask.shape)} does not match the prediction {tuple(prob.shape)}")
+    dice = DiceRegion().per_channel(prob, mask)
+    return torch.stack([dice.double(), hd95_regions(prob, mask)])

@@ -311,3 +311,33 @@ class DiceRegion(DiceCoefficient):
         if mode != "sigmoid":
             raise NotImplementedError("XLSTM_HVED emits sigmoid region maps (SURVEY F7)")
         return self.per_channel(input, target)[{"WT": 0, "TC": 1, "EC": 2}[region]]
+
+
+def hd95_regions(input, target, spacing=(1.0, 1.0, 1.0)):
+    """(3,) fp64 device tensor: HD95 of WT, TC, EC from ONE xh_hd95 call (sigmoid maps, N == 1)."""
+    return ops.hd95(input.detach(), target, spacing)
+
+
+class getHausdorff:
+    """metrics.py:311-406, mode='sigmoid': the 95th-percentile Hausdorff distance of one region, computed on the device.
+
+    Region channels are getHausdorff's (WT, TC, EC = 0, 1, 2, as DiceRegion and SegToMask); 'ET' is accepted for 'EC'.  The
+    surface is the reference's Sobel surface, distances are exact Euclidean distances between the scaled voxel coordinates,
+    P95 is np.percentile's 'linear' rule; 0 when either surface is empty.  Returns a 0-dim fp64 device tensor.
+
+    Cost: xh_hd95 always computes all three regions, so each call here does the work of hd95_regions and keeps one value.
+    Three single-region calls per volume (the evaluation.py:386-389 pattern) cost three times one hd95_regions call; use
+    hd95_regions (or inference.eval_overlap_metrics) when all three are wanted."""
+
+    def __init__(self, spacing=(1.0, 1.0, 1.0)):
+        self.spacing = spacing
+
+    def __call__(self, input, target, region="WT", mode="sigmoid"):
+        if mode != "sigmoid":
+            raise NotImplementedError("XLSTM_HVED emits sigmoid region maps (SURVEY F7)")
+        if region not in ops.HD95_REGIONS:
+            raise ValueError(f"unknown region {region!r}: expected one of {sorted(ops.HD95_REGIONS)}")
+        return hd95_regions(input, target, self.spacing)[ops.HD95_REGIONS[region]]
+
+
+getHausdorff_KD = getHausdorff          # the name evaluation.py:8,386 imports; the same metric on this path

@@ -1858,3 +1858,49 @@ def fill(shape, value, dtype, device, gscale=None):
     out = torch.empty(shape, dtype=dtype, device=device)
     L.check(L.load().xh_fill(_stream(), _dt(out), _p(out), out.numel(), float(value), _p(gscale)), "xh_fill")
     return out
+
+
+# ----------------------------------------------------------------------------------------------- HD95 region metric
+HD95_REGIONS = {"WT": 0, "TC": 1, "EC": 2, "ET": 2}      # getHausdorff's channel map (metrics.py:344-352); 'ET' = 'EC'
+
+
+def _hd95_target_dt(t):
+    if t.dtype in (torch.uint8, torch.bool):
+        return L.XH_U8
+    return _dt(t)
+
+
+def hd95_check(input, target, spacing=(1.0, 1.0, 1.0)):
+    """Argument checks of hd95 that need no device (shapes, N == 1, dtypes, spacing); returns the spacing as 3 floats."""
+    if input.dim() != 5 or tuple(input.shape) != tuple(target.shape):
+        raise ValueError(f"'input' and 'target' must be 5D and of the same shape, got {tuple(input.shape)} vs {tuple(target.shape)}")
+    if input.shape[0] != 1:
+        raise ValueError(f"HD95 is computed for one sample (N == 1), got N = {input.shape[0]}")
+    if input.shape[1] < 3:
+        raise ValueError(f"expected the three region channels (WT, TC, EC), got C = {input.shape[1]}")
+    sp = tuple(float(s) for s in spacing)
+    if len(sp) != 3 or not all(s > 0 for s in sp):
+        raise ValueError(f"spacing must be three positive numbers, got {spacing}")
+    _dt(input)
+    _hd95_target_dt(target)
+    return sp
+
+
+def hd95(input, target, spacing=(1.0, 1.0, 1.0), counts=False):
+    """(3,) fp64 HD95 of the regions WT, TC, EC (xh_hd95): input (1, C >= 3, D, H, W) probabilities (fp32 / bf16 / fp16,
+    thresholded at 0.5), target of the same shape (uint8 / bool / fp32 / bf16 / fp16, != 0).  counts=True also returns the (6,)
+    int64 surface sizes [pred WT, target WT, pred TC, target TC, pred EC, target EC].  No host synchronisation."""
+    sp = hd95_check(input, target, spacing)
+    _, _, d, h, w, _ = _vol(input)
+    _vol(target)
+    lib = L.load()
+    unit = int(sp == (1.0, 1.0, 1.0))
+    nbytes = lib.xh_hd95_workspace_bytes(d, h, w, unit)
+    if nbytes < 0:
+        raise ValueError(f"unsupported extent {(d, h, w)} for xh_hd95 (W <= 512, H and D <= 65535)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=input.device)
+    out = torch.empty(3, dtype=torch.float64, device=input.device)
+    cnt = torch.empty(6, dtype=torch.int64, device=input.device) if counts else None
+    L.check(lib.xh_hd95(_stream(), _dt(input), _p(input), d * h * w, _hd95_target_dt(target), _p(target), d * h * w, d, h, w,
+                        sp[0], sp[1], sp[2], _p(ws), nbytes, _p(out), _p(cnt)), "xh_hd95")
+    return (out, cnt) if counts else out
