@@ -29,6 +29,7 @@ struct VilWs {
   // chunk-recurrent mLSTM: per (batch, head, chunk of 64 tokens) the carried matrix memory C (16x16) + normaliser n (16)
   // in front of the chunk, and the mirror-image state R, r of the backward (contributions of all LATER chunks)
   float *cst, *rst;
+  float* A;                             // per (batch, head, chunk): the anchor of the stored F / G offsets (vil_scan_kernel)
 };
 constexpr int CL = 64;                  // chunk length = one wavefront of tokens
 constexpr int STF = 16 * 16 + 16;       // floats per chunk state
@@ -51,6 +52,7 @@ static long long ws_layout(VilWs* w, float* base, int B, int S, int C) {
   t.rq = take(BS * NH); t.ck = take(BS * NH); t.dscat = take(BS * NH);
   const long long nst = (long long)B * NH * ((S + CL - 1) / CL) * STF;
   t.cst = take(nst); t.rst = take(nst);
+  t.A = take((long long)B * NH * ((S + CL - 1) / CL));
   if (w) *w = t;
   return o;
 }
@@ -210,21 +212,31 @@ __global__ __launch_bounds__(PRE2_TT * NH * (2 * C / NH / 4)) void vil_pre2_kern
 }
 
 // -------------------------------------------------------------------------------------------------
-// gate scans: one 1024-lane workgroup per (batch, head).  F = inclusive cumsum of logsigmoid(f) (fp64 carry),
-// G = inclusive prefix max of g = i - F with its arg index.  A lane owns a short contiguous chunk (4 tokens at
-// S = 4096, so a wave reads 1 KB runs); carries move through wavefront shuffles, then across the 16 waves through LDS.
+// gate scans: one 1024-lane workgroup per (batch, head).  F = inclusive cumsum of logsigmoid(f), G = inclusive prefix max
+// of g = i - F with its arg index, both in fp64.  A lane owns a short contiguous chunk (4 tokens at S = 4096, so a wave reads
+// 1 KB runs); carries move through wavefront shuffles, then across the 16 waves through LDS.
+//
+// |F_t| grows linearly with t (about 4e4 at S = 32 768 with a forget bias of -1), so F and G are NOT stored as they are:
+// in fp32 the weights exp(g_s - G_t) and the floor exp(-(F_t + G_t)) would be differences of numbers of that size and
+// lose digits with the position.  Every 64-token chunk c gets an anchor A_c = fp32(F at its first token); stored are the
+// offsets  F'_t = F_t - A_c(t)  and  G'_t = G_t + A_c(t)  (small: they span one chunk's decay and the gate values).  Then
+//     m_t = F'_t + G'_t,   g_s - G_t = (i_s - F'_s) - G'_t                        for s, t in one chunk,
+//     g_s - G_t = (i_s - F'_s) - G'_t + (A_c(t) - A_c(s))                          across chunks,
+// and the anchor difference is one fp32 subtraction of two fp32 values: the exact difference rounded once.
 // -------------------------------------------------------------------------------------------------
 constexpr int SCAN_T = 1024, SCAN_W = SCAN_T / 64;
+__device__ __forceinline__ float* vil_anchor(const VilWs& w, int bh, int S) { return w.A + (long long)bh * ((S + CL - 1) / CL); }
 __global__ __launch_bounds__(SCAN_T) void vil_scan_kernel(int S, VilWs w) {
   __shared__ double s_sum[SCAN_W];
-  __shared__ float s_max[SCAN_W];
+  __shared__ double s_max[SCAN_W];
   __shared__ int s_arg[SCAN_W];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const long long base = (long long)blockIdx.x * S;
+  float* anc = vil_anchor(w, blockIdx.x, S);
   const int chunk = (S + SCAN_T - 1) / SCAN_T;
   const int t0 = min(S, tid * chunk), t1 = min(S, t0 + chunk);
-  // A lane's chunk is short (4 tokens at S = 4096): it is loaded ONCE into registers -- the three walks over it (sum, prefix + local
-  // maximum, running maximum) were three round trips to memory, the last one re-reading the F this kernel had just written
+  // A lane's chunk is short (4 tokens at S = 4096): it is loaded ONCE into registers -- the walks over it (sum, prefix + local
+  // maximum, running maximum) would otherwise each be a round trip to memory
   constexpr int CH = 8;
   const bool reg = chunk <= CH;                   // block-uniform
   float lfv[CH], gv[CH];
@@ -249,9 +261,10 @@ __global__ __launch_bounds__(SCAN_T) void vil_scan_kernel(int S, VilWs w) {
   }
   if (lane == 63) s_sum[wv] = inc;
   __syncthreads();
-  double run = inc - loc;   // exclusive prefix within the wave ...
-  for (int i = 0; i < wv; ++i) run += s_sum[i];   // ... plus the waves before it
-  float lmax = -INFINITY;
+  double run0 = inc - loc;   // exclusive prefix within the wave ...
+  for (int i = 0; i < wv; ++i) run0 += s_sum[i];   // ... plus the waves before it
+  // pass 1: the anchors (written by the lane that owns a chunk's first token) and the lane's maximum of g
+  double lmax = -INFINITY, run = run0;
   int larg = t0;
   if (reg) {
 #pragma unroll
@@ -259,54 +272,61 @@ __global__ __launch_bounds__(SCAN_T) void vil_scan_kernel(int S, VilWs w) {
       const int t = t0 + k;
       if (t < t1) {
         run += (double)lfv[k];
-        const float Ft = (float)run;
-        w.F[base + t] = Ft;
-        gv[k] -= Ft;                              // g_t = i_t - F_t
-        if (gv[k] > lmax) { lmax = gv[k]; larg = t; }
+        if (t % CL == 0) anc[t / CL] = (float)run;
+        const double g = (double)gv[k] - run;     // g_t = i_t - F_t
+        if (g > lmax) { lmax = g; larg = t; }
       }
     }
   } else {
     for (int t = t0; t < t1; ++t) {
       run += (double)logsigmoid_(w.fg[base + t]);
-      const float Ft = (float)run;
-      w.F[base + t] = Ft;
-      const float g = w.ig[base + t] - Ft;
+      if (t % CL == 0) anc[t / CL] = (float)run;
+      const double g = (double)w.ig[base + t] - run;
       if (g > lmax) { lmax = g; larg = t; }
     }
   }
-  float pm = lmax;
+  double pm = lmax;
   int pa = larg;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    const float um = __shfl_up(pm, o, 64);
+    const double um = __shfl_up(pm, o, 64);
     const int ua = __shfl_up(pa, o, 64);
     if (lane >= o && um >= pm) { pm = um; pa = ua; }   // earlier index wins ties
   }
   if (lane == 63) { s_max[wv] = pm; s_arg[wv] = pa; }
-  __syncthreads();
-  float em = -INFINITY;
+  __syncthreads();                                // also publishes the anchors to the whole workgroup
+  double em = -INFINITY;
   int ea = 0;
   for (int i = 0; i < wv; ++i)
     if (s_max[i] > em) { em = s_max[i]; ea = s_arg[i]; }
-  const float xm = __shfl_up(pm, 1, 64);
+  const double xm = __shfl_up(pm, 1, 64);
   const int xa = __shfl_up(pa, 1, 64);
   if (lane > 0 && xm > em) { em = xm; ea = xa; }
+  // pass 2: running maximum, offsets from the anchors
+  run = run0;
   if (reg) {
 #pragma unroll
     for (int k = 0; k < CH; ++k) {
       const int t = t0 + k;
       if (t < t1) {
-        if (gv[k] > em) { em = gv[k]; ea = t; }
-        w.G[base + t] = em;
+        run += (double)lfv[k];
+        const double g = (double)gv[k] - run;
+        if (g > em) { em = g; ea = t; }
+        const double A = (double)anc[t / CL];
+        w.F[base + t] = (float)(run - A);
+        w.G[base + t] = (float)(em + A);
         w.arg[base + t] = ea;
       }
     }
     return;
   }
   for (int t = t0; t < t1; ++t) {
-    const float g = w.ig[base + t] - w.F[base + t];
+    run += (double)logsigmoid_(w.fg[base + t]);
+    const double g = (double)w.ig[base + t] - run;
     if (g > em) { em = g; ea = t; }
-    w.G[base + t] = em;
+    const double A = (double)anc[t / CL];
+    w.F[base + t] = (float)(run - A);
+    w.G[base + t] = (float)(em + A);
     w.arg[base + t] = ea;
   }
 }
@@ -385,6 +405,7 @@ __global__ __launch_bounds__(256) void mlstm_fwd_kernel(int S, VilWs w) {
   const long long hb = ((long long)b * NH + h) * S;
   const int t0 = (blockIdx.x / MSPLIT) * 32, ks = blockIdx.x % MSPLIT;
   const int t = t0 + wv * 8 + (lane >> 3), sl = lane & 7;
+  const float* anc = vil_anchor(w, b * NH + h, S);
   const bool tv = t < S;
   float q[DH], num[DH];
   float den = 0.f, Gt = 0.f;
@@ -401,7 +422,10 @@ __global__ __launch_bounds__(256) void mlstm_fwd_kernel(int S, VilWs w) {
       s_k[r * LD + c] = s < S ? w.k[(hb + s) * DH + c] : 0.f;
       s_v[r * LD + c] = s < S ? w.v[(hb + s) * DH + c] : 0.f;
     }
-    if (tid < KT) { const int s = st0 + tid; s_g[tid] = s < S ? w.ig[hb + s] - w.F[hb + s] : -INFINITY; }
+    if (tid < KT) {                                  // anchor of the query block (one chunk) minus that of the key tile
+      const int s = st0 + tid;
+      s_g[tid] = s < S ? w.ig[hb + s] - w.F[hb + s] + (anc[t0 / CL] - anc[st0 / CL]) : -INFINITY;
+    }
     __syncthreads();
 #pragma unroll 2
     for (int jj = 0; jj < KT / 8; ++jj) {
@@ -576,6 +600,7 @@ __global__ __launch_bounds__(320) void mlstm_chunk_scan_kernel(int S, int nchunk
   const bool live = e < STF;
   const long long hb = (long long)blockIdx.x * S;
   float* st = (REV ? w.rst : w.cst) + (long long)blockIdx.x * nchunk * STF;
+  const float* anc = vil_anchor(w, blockIdx.x, S);
   float run = 0.f;
   for (int b0 = 0; b0 < nchunk; b0 += SCB) {
     // chunk index of position i of this block, in scan order (forward: ascending, reverse: descending)
@@ -584,8 +609,9 @@ __global__ __launch_bounds__(320) void mlstm_chunk_scan_kernel(int S, int nchunk
     if (e < SCB && b0 + e < nchunk) {
       const int c = cidx(e);
       float dec;
-      if (!REV) dec = c > 0 ? expf(w.G[hb + c * CL - 1] - w.G[hb + min(S, (c + 1) * CL) - 1]) : 0.f;
-      else dec = c < nchunk - 1 ? expf(w.G[hb + c * CL] - w.G[hb + (c + 1) * CL]) : 0.f;
+      // G of two chunks: offsets from two anchors (vil_scan_kernel)
+      if (!REV) dec = c > 0 ? expf(w.G[hb + c * CL - 1] - w.G[hb + min(S, (c + 1) * CL) - 1] + (anc[c] - anc[c - 1])) : 0.f;
+      else dec = c < nchunk - 1 ? expf(w.G[hb + c * CL] - w.G[hb + (c + 1) * CL] + (anc[c + 1] - anc[c])) : 0.f;
       s_dec[e] = dec;
     }
     float d[SCB];
@@ -674,7 +700,8 @@ __global__ __launch_bounds__(256) void mlstm_chunk_fwd_kernel(int S, int nchunk,
     accI = MFMA4(a, s_C[(k0 + sg) * 16 + kj], accI);          // (C^T q_t)[j]
     accN = MFMA4(a, s_C[256 + k0 + sg], accN);                // q_t . n   (every column)
   }
-  const float Mc = c > 0 ? w.G[hb + s_base - 1] : 0.f;
+  const float* anc = vil_anchor(w, b * NH + h, S);
+  const float Mc = c > 0 ? w.G[hb + s_base - 1] + (anc[c] - anc[c - 1]) : 0.f;    // in this chunk's anchor frame
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int tl = 16 * wv + sg * 4 + r;
@@ -701,6 +728,7 @@ __global__ __launch_bounds__(256) void mlstm_chunk_bwd_kernel(int S, int nchunk,
   const int kj = lane & 15, sg = lane >> 4;
   const long long hb = ((long long)b * NH + h) * S;
   const int s_base = c * CL, nv = min(CL, S - s_base);
+  const float* anc = vil_anchor(w, b * NH + h, S);
   chunk_load_rows(s_q, w.q, hb + s_base, nv, tid);
   chunk_load_rows(s_k, w.k, hb + s_base, nv, tid);
   chunk_load_rows(s_v, w.v, hb + s_base, nv, tid);
@@ -751,7 +779,7 @@ __global__ __launch_bounds__(256) void mlstm_chunk_bwd_kernel(int S, int nchunk,
 #pragma unroll
     for (int k0 = 0; k0 < 16; k0 += 4)              // (C da'_t)[j] = sum_k C[j][k] da'_t[k]
       accX = MFMA4(s_da[(16 * wv + kj) * CLD + k0 + sg], s_C[kj * 16 + k0 + sg], accX);
-    const float Mc = c > 0 ? w.G[hb + s_base - 1] : 0.f;
+    const float Mc = c > 0 ? w.G[hb + s_base - 1] + (anc[c] - anc[c - 1]) : 0.f;  // in this chunk's anchor frame
     const float nj = s_C[256 + kj];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -775,7 +803,7 @@ __global__ __launch_bounds__(256) void mlstm_chunk_bwd_kernel(int S, int nchunk,
       xK = MFMA4(s_v[(16 * wv + kj) * CLD + k0 + sg], s_R[kj * 16 + k0 + sg], xK);     // (R v_s)[j]
       xV = MFMA4(s_k[(16 * wv + kj) * CLD + k0 + sg], s_R[(k0 + sg) * 16 + kj], xV);   // (R^T k_s)[j]
     }
-    const float Mr = later ? w.G[hb + s_base + CL] : 0.f;
+    const float Mr = later ? w.G[hb + s_base + CL] + (anc[c] - anc[c + 1]) : 0.f;  // in this chunk's anchor frame
     const float rj = s_R[256 + kj];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -930,6 +958,7 @@ __global__ __launch_bounds__(256) void mlstm_bwd_q_kernel(int S, VilWs w) {
   const long long hb = ((long long)b * NH + h) * S;
   const int t0 = (blockIdx.x / MSPLIT) * 32, ks = blockIdx.x % MSPLIT;
   const int t = t0 + wv * 8 + (lane >> 3), sl = lane & 7;
+  const float* anc = vil_anchor(w, b * NH + h, S);
   const bool tv = t < S;
   float da[DH], dq[DH];
   float db = 0.f, Gt = 0.f;
@@ -946,7 +975,10 @@ __global__ __launch_bounds__(256) void mlstm_bwd_q_kernel(int S, VilWs w) {
       s_k[r * LD + c] = s < S ? w.k[(hb + s) * DH + c] : 0.f;
       s_v[r * LD + c] = s < S ? w.v[(hb + s) * DH + c] : 0.f;
     }
-    if (tid < KT) { const int s = st0 + tid; s_g[tid] = s < S ? w.ig[hb + s] - w.F[hb + s] : -INFINITY; }
+    if (tid < KT) {                                  // anchor of the query block (one chunk) minus that of the key tile
+      const int s = st0 + tid;
+      s_g[tid] = s < S ? w.ig[hb + s] - w.F[hb + s] + (anc[t0 / CL] - anc[st0 / CL]) : -INFINITY;
+    }
     __syncthreads();
 #pragma unroll 2
     for (int jj = 0; jj < KT / 8; ++jj) {
@@ -997,6 +1029,7 @@ __global__ __launch_bounds__(256) void mlstm_bwd_kv_kernel(int S, VilWs w) {
   const int s0 = (blockIdx.x / MSPLIT) * 32, ks = blockIdx.x % MSPLIT;
   const int s = s0 + wv * 8 + (lane >> 3), sl = lane & 7;
   const bool sv = s < S;
+  const float* anc = vil_anchor(w, b * NH + h, S);
   float kk[DH], vv[DH], dk[DH], dv[DH];
   float gs = 0.f;
 #pragma unroll
@@ -1017,7 +1050,7 @@ __global__ __launch_bounds__(256) void mlstm_bwd_kv_kernel(int S, VilWs w) {
     }
     if (tid < QT) {
       const int t = qt0 + tid;
-      s_G[tid] = t < S ? w.G[hb + t] : INFINITY;
+      s_G[tid] = t < S ? w.G[hb + t] - (anc[qt0 / CL] - anc[s0 / CL]) : INFINITY;   // query tile's anchor minus the key block's
       s_db[tid] = t < S ? w.dbp[hb + t] : 0.f;
     }
     __syncthreads();
