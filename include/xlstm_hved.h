@@ -722,6 +722,53 @@ int xh_hd95(void* stream, int in_dtype, const void* input, long long in_cstride,
             long long* counts);
 
 /* ------------------------------------------------------------------------------------------------
+ * Training-time augmentation (transform.py:10-28 as train.py:121 configures it, applied at BraTSdataset.py:389-390) on volumes
+ * resident on the device (csrc/augment.hip).  A volume is 4 channels of D x H x W (fp32 or int16, channel c at img + c*D*H*W)
+ * and a D x H x W uint8 label map.  Order of the reference: IntensityScale, IntensityShift, RandomFlip, Random_Crop_3D,
+ * Normalize (/ 255), SegToMask.  RandomRotate / Scale (scipy interpolation, unused by train.py) are not provided.
+ * ------------------------------------------------------------------------------------------------ */
+#define XH_I16 4                  /* augmentation source storage: int16 (values converted to fp32 exactly) */
+#define XH_AUG_SCALE 1           /* xh_aug_draw / xh_aug_apply flags */
+#define XH_AUG_SHIFT 2
+#define XH_AUG_FLIP 4
+#define XH_AUG_NORMALIZE 8
+#define XH_AUG_RNG_STREAM 160     /* Philox stream id of the augmentation draws (xh_poe_multi uses the latent levels 0..3) */
+typedef struct {
+  const void* img; const unsigned char* lab;   /* device pointers */
+  int D, H, W, dtype;                          /* dtype: XH_F32 | XH_I16 */
+} xh_aug_volume;
+/* One sample's parameters (32 bytes).  scale / shift: the alphas of IntensityScale / IntensityShift (1.0 / 0.0 when off);
+ * origin: the crop origin (d, h, w) in the FLIPPED volume; flip: bit 0 = flip D, bit 1 = flip H (the reference's RandomFlip
+ * acts on (1, D, H, W) arrays: its first axis is the singleton, so W never flips). */
+typedef struct { double scale, shift; int origin[3]; int flip; } xh_aug_params;
+/* Per (volume, channel), over the voxels != 0 of the whole volume: out[4 c + 0..3] = {count, mean, std (ddof 0), 0} in fp64
+ * (count 0: mean = std = 0).  Per-block fp64 sums of x and x^2 reduced in a fixed order: bit-identical from run to run, no atomics.
+ * Two launches; ws_bytes >= xh_aug_moments_workspace_bytes(D, H, W). */
+long long xh_aug_moments_workspace_bytes(int D, int H, int W);
+int xh_aug_moments(void* stream, const xh_aug_volume* vol, void* ws, long long ws_bytes, double* out);
+/* Draws the parameters of N samples: vols = the device table of volumes, idx[n] (device int32) = sample n's row of it,
+ * crop[3] = output extent (host memory; a volume smaller than it gets origin -1 and comes out NaN from xh_aug_apply).  flags:
+ * XH_AUG_SCALE | XH_AUG_SHIFT | XH_AUG_FLIP select the draws (the others get identity parameters).  rng: two device words
+ * {seed, counter}; the launch (one workgroup) draws with `counter` and advances it by one, so every launch -- every replay of a
+ * captured graph -- draws afresh.
+ * Words: B_j = Philox4x32-10 of counter block (i = 4 n + j, stream XH_AUG_RNG_STREAM, counter, seed), the block layout of
+ * xh_philox_normal; W(a, b) = (a << 32 | b) as uint64; U(a, b) = (W(a, b) >> 11) * 2^-53 in [0, 1); R(a, b, r) = floor(W * r / 2^64).
+ *   scale = (1 - s_scale) + (2 s_scale) * U(B0[0], B0[1])        shift = (-s_shift) + (2 s_shift) * U(B0[2], B0[3])
+ *   origin[0..2] = R(B1[0], B1[1], D - d), R(B1[2], B1[3], H - h), R(B2[0], B2[1], W - w)   (0 when the extent equals the crop)
+ *   flip D = U(B2[2], B2[3]) > p,  flip H = U(B3[0], B3[1]) > p   (U(B3[2], B3[3]): the reference's third draw, flips nothing)
+ * fp64 arithmetic, one rounding per operation (no contraction).  Each parameter owns its words whatever the flags are. */
+int xh_aug_draw(void* stream, const xh_aug_volume* vols, int nvol, const int* idx, int N, const int* crop, int flags,
+                double s_scale, double s_shift, double flip_prob, unsigned long long* rng, xh_aug_params* params);
+/* Builds N samples: x (N, 4, d, h, w) in x_dtype (XH_F32 | XH_BF16 | XH_F16), mask (N, 3, d, h, w) in m_dtype.  Voxel (z, y, u)
+ * of sample n reads source (fd(o0 + z), fh(o1 + y), o2 + u) of volume idx[n] (fd(i) = D-1-i when flipping D, else i; same for H),
+ * then v = v * (float)scale [XH_AUG_SCALE]; v != 0: v = v + (float)((float)scale * std_c) * (float)shift [XH_AUG_SHIFT];
+ * v = v / 255 [XH_AUG_NORMALIZE]; each an fp32 operation with one rounding, then rounded to nearest-even into x_dtype.  mask = (l > 0, l in {1, 2, 3}, l == 1).
+ * moments: the (nvol, 4, 4) rows of xh_aug_moments.  Parameters outside the volume (or idx outside [0, nvol)): the sample's x is
+ * NaN and its mask 0.  One launch, no host synchronisation. */
+int xh_aug_apply(void* stream, const xh_aug_volume* vols, int nvol, const double* moments, const int* idx,
+                 const xh_aug_params* params, int N, int d, int h, int w, int flags, int x_dtype, void* x, int m_dtype, void* mask);
+
+/* ------------------------------------------------------------------------------------------------
  * Discriminator (RA_HVED.py:204-236, buildingblocks.py:342-358): convolutions 7 -> 64 -> 128 -> 256 -> 512 -> 1 with kernel
  * size ks = 4 (train.py:146, Pretrain.py:150) or 3 (the class default), padding 1, strides 1,2,2,2,1, as implicit GEMMs on the
  * matrix cores.  Inside the discriminator activations are CHANNELS-LAST [N][D][H][W][C], 16-bit (dtype XH_BF16 / XH_F16),

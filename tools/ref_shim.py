@@ -99,3 +99,28 @@ def build_reference_model(ns, seed=1, cls="XLSTM_HVED", dtype=None, **overrides)
     if dtype is not None:
         model = model.to(dtype)
     return model
+
+
+def load_transform():
+    """The reference's transform.py (its own code) with torchvision.transforms.Compose restated (apply the list in order)
+    and skimage stubbed (only Scale uses skimage.transform.rescale; train.py does not use Scale)."""
+    import torch  # noqa: F401  (before the stubs: torch's import inspects every loaded module)
+
+    class Compose:
+        def __init__(self, transforms):
+            self.transforms = transforms
+
+        def __call__(self, x):
+            for t in self.transforms:
+                x = t(x)
+            return x
+
+    _stub("torchvision")
+    _stub("torchvision.transforms", Compose=Compose, ToTensor=_Anything)
+    sys.modules["torchvision.transforms"].Compose = Compose
+    _stub("skimage")
+    _stub("skimage.transform")
+    if REF_ROOT not in sys.path:
+        sys.path.insert(0, REF_ROOT)
+    import transform as ref_transform
+    return ref_transform

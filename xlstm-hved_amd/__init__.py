@@ -13,7 +13,8 @@ from .model import (MODELS, SUBSETS_MODALITIES, AbstractFusion3DUNet, ReconDecod
                     U_HVEDConvNet3D, U_HVEDConvXLSTMNet3D, XLSTM_HVED, XLSTM_HVED_woDuSFE, XLSTM_HVED_woSMVAE,
                     XLSTM_HVED_woViL, find_model_using_name)
 from .utils import init_weights, seed_everything, subset_idx  # noqa: F401
-from . import inference, losses  # noqa: F401
+from . import augment, inference, losses  # noqa: F401
+from .augment import VolumeBank  # noqa: F401
 from .losses import (DiceCoefficient, DiceLoss, DiceRegion, GANLoss, MSELoss, combine, compute_KLD, compute_KLD_levels,  # noqa: F401
                      gan_pair_loss, getHausdorff, getHausdorff_KD, hd95_regions, mse_loss,
                      nested_attention)

@@ -10,6 +10,9 @@ LIB_PATH = os.path.join(_HERE, "lib", "libxlstm_hved_hip.so")
 
 XH_F32, XH_BF16, XH_F16 = 0, 1, 2
 XH_U8 = 3                                    # uint8 / bool storage (xh_hd95 targets)
+XH_I16 = 4                                   # int16 augmentation sources (xh_aug_*)
+XH_AUG_SCALE, XH_AUG_SHIFT, XH_AUG_FLIP, XH_AUG_NORMALIZE = 1, 2, 4, 8
+XH_AUG_RNG_STREAM = 160
 ARITH_F32_SPLIT, ARITH_K7_VECTOR = 1, 2      # xh_conv_desc.arith bits
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SIGMOID = 0, 1, 2, 3
 
@@ -107,6 +110,13 @@ class VilParams(C.Structure):
     _fields_ = [(n, vp) for n in VIL_FIELDS]
 
 
+class AugVolume(C.Structure):
+    _fields_ = [("img", vp), ("lab", vp), ("D", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int)]
+
+
+AUG_PARAMS_BYTES = 32   # sizeof(xh_aug_params): {double scale, shift; int origin[3], flip}
+
+
 # name -> (restype, argtypes); mirrors include/xlstm_hved.h one to one
 I, F = C.c_int, C.c_float
 SIGNATURES = {
@@ -201,6 +211,10 @@ SIGNATURES = {
     "xh_kld_bwd": (I, [vp, I, vp, vp, vp, I, I, ll, F, vp, vp, vp]),
     "xh_hd95_workspace_bytes": (ll, [I, I, I, I]),
     "xh_hd95": (I, [vp, I, vp, ll, I, vp, ll, I, I, I, C.c_double, C.c_double, C.c_double, vp, ll, vp, vp]),
+    "xh_aug_moments_workspace_bytes": (ll, [I, I, I]),
+    "xh_aug_moments": (I, [vp, C.POINTER(AugVolume), vp, ll, vp]),
+    "xh_aug_draw": (I, [vp, vp, I, vp, I, C.POINTER(I), I, C.c_double, C.c_double, C.c_double, vp, vp]),
+    "xh_aug_apply": (I, [vp, vp, I, vp, vp, vp, I, I, I, I, I, I, vp, I, vp]),
     "xh_nested_weight": (I, [vp, I, vp, ll, vp, ll, I, ll]),
     "xh_fill": (I, [vp, I, vp, ll, F, vp]),
     "xh_scalar_lincomb": (I, [vp, I, vp, vp, vp, vp]),

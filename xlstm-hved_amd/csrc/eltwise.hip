@@ -1400,24 +1400,7 @@ extern "C" int xh_init_fold_bwd(void* stream, const double* red_x, long long cou
 
 // ---------------------------------------------------------------------------------------- product of experts
 #define POE_EPS 1e-8f
-// Philox4x32-10 (Salmon et al., SC'11; the generator behind torch's device RNG): counter-based, so element i of draw c is a pure
-// function of (seed, c, stream, i) -- the backward pass regenerates the forward's noise instead of reading it from HBM.
-struct PhiloxKey { unsigned long long seed, ctr; int stream; };
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-__device__ __forceinline__ void philox_block(const PhiloxKey& k, long long i, unsigned (&o)[4]) {
-  philox4x32_10((unsigned)i, (unsigned)((unsigned long long)i >> 32) | ((unsigned)k.stream << 24), (unsigned)k.ctr, (unsigned)(k.ctr >> 32),
-                (unsigned)k.seed, (unsigned)(k.seed >> 32), o);
-}
+// Philox4x32-10: PhiloxKey / philox_block in common.h (shared with the augmentation draws of augment.hip)
 // one standard normal per element (Box-Muller on two 24-bit uniforms in (0, 1): |eps| <= 5.8)
 __device__ __forceinline__ float philox_normal(const PhiloxKey& k, long long i) {
   unsigned o[4];

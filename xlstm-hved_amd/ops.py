@@ -1904,3 +1904,47 @@ def hd95(input, target, spacing=(1.0, 1.0, 1.0), counts=False):
     L.check(lib.xh_hd95(_stream(), _dt(input), _p(input), d * h * w, _hd95_target_dt(target), _p(target), d * h * w, d, h, w,
                         sp[0], sp[1], sp[2], _p(ws), nbytes, _p(out), _p(cnt)), "xh_hd95")
     return (out, cnt) if counts else out
+
+
+# ------------------------------------------------------------------------------------------------ training augmentation
+def aug_moments(vol, out):
+    """xh_aug_moments: vol = a _lib.AugVolume of one registered volume; out = (4, 4) fp64 device rows {count, mean, std, 0} of
+    each channel's nonzero voxels (fixed reduction order: bit-identical from run to run)."""
+    lib = L.load()
+    nbytes = lib.xh_aug_moments_workspace_bytes(vol.D, vol.H, vol.W)
+    if nbytes < 0:
+        raise ValueError(f"bad volume extent {(vol.D, vol.H, vol.W)}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
+    L.check(lib.xh_aug_moments(_stream(), C.byref(vol), _p(ws), nbytes, _p(out)), "xh_aug_moments")
+    return out
+
+
+def aug_draw(table, nvol, idx, crop, flags, s_scale, s_shift, flip_prob, rng, params):
+    """xh_aug_draw: parameters of len(idx) samples into `params` ((N, 32) uint8 device rows of xh_aug_params); advances the
+    device generator words `rng` ({seed, counter}, int64) by one draw.  No host synchronisation."""
+    if rng.dtype != torch.int64 or rng.numel() != 2 or not rng.is_cuda:
+        raise ValueError("rng: two int64 device words {seed, counter}")
+    c3 = (C.c_int * 3)(*[int(v) for v in crop])
+    L.check(L.load().xh_aug_draw(_stream(), _p(table), int(nvol), _p(idx), int(idx.numel()), c3, int(flags), float(s_scale),
+                                 float(s_shift), float(flip_prob), _p(rng), _p(params)), "xh_aug_draw")
+    return params
+
+
+_AUG_DT = {torch.float32: L.XH_F32, torch.bfloat16: L.XH_BF16, torch.float16: L.XH_F16}
+
+
+def aug_apply(table, nvol, moments, idx, params, flags, x, mask):
+    """xh_aug_apply: x (N, 4, d, h, w) and mask (N, 3, d, h, w), contiguous, fp32 / bf16 / fp16, written in one launch."""
+    if x.dim() != 5 or mask.dim() != 5 or x.shape[1] != 4 or mask.shape[1] != 3 or x.shape[0] != mask.shape[0] \
+            or x.shape[2:] != mask.shape[2:]:
+        raise ValueError(f"x must be (N, 4, d, h, w) and mask (N, 3, d, h, w), got {tuple(x.shape)} and {tuple(mask.shape)}")
+    if not (x.is_contiguous() and mask.is_contiguous()):
+        raise ValueError("x and mask must be contiguous")
+    if x.dtype not in _AUG_DT or mask.dtype not in _AUG_DT:
+        raise ValueError(f"x / mask storage must be fp32, bf16 or fp16, got {x.dtype} / {mask.dtype}")
+    n, _, d, h, w = x.shape
+    if idx.numel() != n or params.shape[0] != n:
+        raise ValueError(f"{n} samples but {idx.numel()} indices and {params.shape[0]} parameter rows")
+    L.check(L.load().xh_aug_apply(_stream(), _p(table), int(nvol), _p(moments), _p(idx), _p(params), n, d, h, w, int(flags),
+                                  _AUG_DT[x.dtype], _p(x), _AUG_DT[mask.dtype], _p(mask)), "xh_aug_apply")
+    return x, mask

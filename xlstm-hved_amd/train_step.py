@@ -345,6 +345,19 @@ class TrainStep:
             for dst_l, src_l in zip(self._seps, eps_lists):
                 for d_, s_ in zip(dst_l, src_l):
                     d_.copy_(s_)
+        return self._launch(update)
+
+    def replay_augmented(self, bank, indices, subset_index_list, transform, update=True):
+        """replay() with the batch built on the device: `transform` (augment.transforms(...)) draws its parameters and writes
+        the augmented volumes bank[indices] straight into the captured static input buffers (no host copy of the batch,
+        BraTSdataset.py:389-390 + train.py:211-212), then the graph runs.  The parameters stay in transform.last_params."""
+        if self._graph is None:
+            raise RuntimeError("TrainStep.capture() has not been called")
+        transform(bank, indices, out=(self._sx, self._smask))
+        self._skeep.copy_(self.keep_mask(subset_index_list, self._sx.shape[0]))
+        return self._launch(update)
+
+    def _launch(self, update):
         self._graph.replay()
         if self._graph2 is not None:
             self.reduce_generator()                          # on the communication stream, under the second graph
